@@ -62,7 +62,12 @@ def parse():
     ap.add_argument("--no-alt", action="store_true", help="skip the extra opt-in bf16x3 measurement and the full-size parity leg")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true", help="do not bracket conv launches with events")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def synth_batch(n, device, seed, channels=1, hr_px=HR):
@@ -180,6 +185,53 @@ def full_size_parity(sr, res_blocks, dev, workload):
     return out
 
 
+DUMP_SAMPLE = 1 << 21          # elements of each sampled generator array (8 MB in fp32)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(stepper, out_dir):
+    """What the last timed step computed, as float32 .npy files in out_dir:
+      loss.g_loss, loss.d_loss.<k>, loss.parts.<k>.<name>   the tensors of the step's return value (train.Stepper.step)
+      generator.{param,exp_avg,exp_avg_sq}                   the updated weights and Adam moments of the generator: its trainable
+                                                             parameters flattened in named_parameters() order, sampled at
+                                                             DUMP_SAMPLE sorted indices drawn from a CPU generator seeded with 0
+      discriminator<k>.{param,exp_avg,exp_avg_sq}            the same for each discriminator, in full
+    The files hold at most DUMP_LIMIT_BYTES together.  Returns their names."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+
+    def losses(prefix, v):
+        if isinstance(v, dict):
+            for k, x in v.items():
+                losses(f"{prefix}.{k}", x)
+        elif torch.is_tensor(v):
+            arrays[prefix] = v.detach().float().cpu().numpy()
+    losses("loss", stepper.last)
+
+    def module_state(prefix, module, opt, sample):
+        ps = [p for _, p in module.named_parameters() if p.requires_grad]
+        flat = {"param": torch.cat([p.detach().reshape(-1) for p in ps])}
+        for key in ("exp_avg", "exp_avg_sq"):     # (no state yet: that optimizer has not stepped, its moments are still zero)
+            flat[key] = torch.cat([opt.state[p].get(key, torch.zeros_like(p)).reshape(-1) for p in ps])
+        idx = None
+        if sample and flat["param"].numel() > DUMP_SAMPLE:
+            g = torch.Generator(device="cpu").manual_seed(0)
+            idx = torch.randint(flat["param"].numel(), (DUMP_SAMPLE,), generator=g).sort().values.to(flat["param"].device)
+        for key, t in flat.items():
+            arrays[f"{prefix}.{key}"] = (t if idx is None else t[idx]).float().cpu().numpy()
+    module_state("generator", stepper.generator, stepper.optimizer_G, True)
+    for k, D in stepper.discriminators.items():
+        module_state(f"discriminator{k}", D, stepper.optimizer_D[k], False)
+
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def self_launch(n):
     """`python bench.py --gpus N` without a launcher: run `torch.distributed.run` with N ranks on this node as a child
     process (never an exec: this process stays a plain parent that has not initialised the GPU) and return its exit code."""
@@ -293,6 +345,9 @@ def main():
         return tmax.item(), ktimes, stepper, (lr_img, hr_img)
 
     dt, ktimes, stepper, (lr_img, hr_img) = measure(args.workload, precision, batch, args.steps, args.warmup, not args.no_kernel_timing)
+    dumped = None
+    if args.dump_outputs and rank == 0:           # (before the extra measurements below step the same stepper again)
+        dumped = dump_outputs(stepper, args.dump_outputs)
 
     # ---- extra, outside the headline: the opt-in split-bf16 mode on the same workload (every rank takes part)
     alt = None
@@ -446,6 +501,8 @@ def main():
             out["configs"] = subs
         if comm_info is not None:
             out["comm"] = comm_info
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "arrays": dumped}
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.destroy_process_group()

@@ -571,6 +571,8 @@ class PackTable:
 
     def add(self, src: torch.Tensor, dst: torch.Tensor, *, M, k_off, k_len, K_total, transpose=False, c_begin=0, ps=False, scale=1.0):
         assert src.dim() == 4 and src.shape[2] == 3 and src.shape[3] == 3 and src.is_contiguous()
+        if not (src.is_cuda and dst.is_cuda):       # the pack kernel dereferences both: a host pointer faults the GPU
+            raise RuntimeError("super-resolution_amd: weight packing only runs on ROCm GPU tensors (no CPU fallback)")
         e = PackEntry()
         e.src, e.dst = src.data_ptr(), dst.data_ptr()
         e.src_cout, e.src_cin = src.shape[0], src.shape[1]

@@ -223,6 +223,7 @@ class Markovian_Discriminator(nn.Module):
         self._packed = None
 
     def forward(self, img, *args):
+        ops._require_gpu(img)                        # (before the weights are packed)
         convs = [m for m in self.model if isinstance(m, nn.Conv2d)]
         if self._packed is None or len(self._packed.convs) != len(convs):
             self._packed = ops.PackedConvs(convs)
@@ -312,6 +313,8 @@ class Conditional_Discriminator(nn.Module):
         self._packed = None
 
     def forward(self, img, cond):
+        ops._require_gpu(img)                        # (before the weights are packed)
+        ops._require_gpu(cond)
         seqs = (self.model_hr, self.model_c, self.endmodel)
         convs = [[m for m in seq if isinstance(m, nn.Conv2d)] for seq in seqs]
         if self._packed is None:

@@ -12,7 +12,7 @@ import sys
 import torch
 from torch.profiler import ProfilerActivity, profile
 
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 train = importlib.import_module("super-resolution_amd.train")
 

@@ -2,7 +2,7 @@
 same build and flags must print identical lines; so must SRK_D_OVERLAP=0 and =1 (the schedule must not change a single bit)."""
 import importlib, os, sys
 import torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 train = importlib.import_module("super-resolution_amd.train")
 torch.manual_seed(0)
 st = train.Stepper(workload="gan", res_blocks=23, device=torch.device("cuda"), hr=256, factor=4)

@@ -2,7 +2,7 @@
 # register / spill figures of the 16-bit conv kernels + where the chain kernel's scratch accesses sit relative to its MFMAs
 # (M = v_mfma, L / S = scratch load / store, | = s_barrier)
 set -e
-B=/root/repo/super-resolution_amd/csrc/build
+B=$(cd "$(dirname "$0")/../.." && pwd)/super-resolution_amd/csrc/build
 O=$B/srk_conv_h16.o
 cd /tmp && rm -rf h16dis && mkdir h16dis && cd h16dis
 (cd $B && /opt/rocm/lib/llvm/bin/llvm-objdump --offloading srk_conv_h16.o > /dev/null) && mv $B/srk_conv_h16.o.0.hipv4-amdgcn-amd-amdhsa--gfx950 dev.o && rm -f $B/srk_conv_h16.o.0.host-*

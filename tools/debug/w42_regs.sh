@@ -2,7 +2,7 @@
 # register / spill figures of the wino42 kernels + where the chain kernel's scratch accesses sit relative to its MFMAs
 # (m = one phase of 12 v_mfma, M = a single one, L / S = scratch load / store, | = s_barrier)
 set -e
-B=/root/repo/super-resolution_amd/csrc/build
+B=$(cd "$(dirname "$0")/../.." && pwd)/super-resolution_amd/csrc/build
 cd /tmp && rm -rf w42dis && mkdir w42dis && cd w42dis
 (cd $B && /opt/rocm/lib/llvm/bin/llvm-objdump --offloading srk_conv_w42.o > /dev/null) && mv $B/srk_conv_w42.o.0.hipv4-amdgcn-amd-amdhsa--gfx950 dev.o && rm -f $B/srk_conv_w42.o.0.host-*
 /opt/rocm/lib/llvm/bin/llvm-readelf --notes dev.o | grep -E "\.name:|vgpr_count|vgpr_spill|sgpr_spill|agpr_count|private_segment_fixed" | paste - - - - - - | sed 's/  */ /g' | cut -c1-230
