@@ -337,6 +337,45 @@ int srk_soft_hist_bwd(const float* x, long n, const float* centers, const float*
 int srk_jet_extract(const float* rows, int B, int L, int row_stride, int etaBins, int phiBins, float threshold, float* out,
                     void* stream);
 
+/* ---- Jet observables of the evaluation loop (evaluation/eval.py's MultHist modes, 44-95 and 314-379; srk_eval.hip).
+ * srk_eval_image_stats: ONE workgroup per image of x [B][H][W] fp32 (element strides sb / sh / sw: any strided batch view of a
+ * one-channel NCHW tensor), H, W <= 512; fills, per image b:
+ *   stats[b][SRK_EVAL_*]  fp64: max, min, sum, count(x > thr), sum of those, NaN flag (0 / 1), and the massless jet four-momentum
+ *                         sum(E, px, py, pz) over every pixel != 0 at the bin centres of eval.py:44-75 (bins = H on both axes)
+ *   topv[b][K], topi[b][K] the K largest values, descending, duplicates counted, with their flat positions r * W + c; among equal
+ *                         values the lowest position first (-0 and +0 are equal).  1 <= K <= min(SRK_EVAL_MAX_K, H * W)
+ *   ties[b][r]            r < min(K, SRK_EVAL_TIES): count of pixels equal to topv[b][r]
+ *   fwm[b][p]             p < n_fwm: Fox-Wolfram moment FWM(l = fwm_l[p], j = fwm_j[p]) over topv/topi[b][0..j) (eval.py:78-95),
+ *                         1 <= j <= K, 0 <= l <= SRK_EVAL_MAX_L; fwm may be null when n_fwm == 0
+ * Deterministic: the top K come from a radix select over the order-preserving bit pattern (4 passes of 8 bits) and an ordered
+ * compaction, never from arrival order; every sum is fixed-order.  No workspace.
+ * srk_eval_pixel_counts: per pixel (r, c), over the B images in order: count[r][c] += #(x > thr); with energy != null also
+ * energy[r][c] += sum_b max(x, thr) * #(x > thr)  (NaN propagates like np.clip).  count / energy: dense [H][W] fp64, accumulated
+ * across calls (the caller zeroes them): SumRaster / MeanImage (utils.py:275-328) before their fold / normalisation. */
+#define SRK_EVAL_MAX_K 64
+#define SRK_EVAL_TIES 9
+#define SRK_EVAL_MAX_FWM 16
+#define SRK_EVAL_MAX_L 32
+enum { SRK_EVAL_MAX = 0, SRK_EVAL_MIN = 1, SRK_EVAL_SUM = 2, SRK_EVAL_NNZ = 3, SRK_EVAL_NNZ_SUM = 4, SRK_EVAL_NAN = 5,
+       SRK_EVAL_E = 6, SRK_EVAL_PX = 7, SRK_EVAL_PY = 8, SRK_EVAL_PZ = 9, SRK_EVAL_NSTAT = 10 };
+typedef struct srk_eval_args {
+  const float* x;
+  int32_t B, H, W;
+  int64_t sb, sh, sw;
+  float thr;
+  int32_t K;
+  int32_t n_fwm;
+  int32_t fwm_l[SRK_EVAL_MAX_FWM], fwm_j[SRK_EVAL_MAX_FWM];
+  double* stats;            /* [B][SRK_EVAL_NSTAT] */
+  float* topv;              /* [B][K] */
+  int32_t* topi;            /* [B][K] */
+  int32_t* ties;            /* [B][SRK_EVAL_TIES] (entries r >= K are left alone) */
+  double* fwm;              /* [B][n_fwm] */
+} srk_eval_args;
+int srk_eval_image_stats(const srk_eval_args* a, void* stream);
+int srk_eval_pixel_counts(const float* x, int B, int H, int W, int64_t sb, int64_t sh, int64_t sw, float thr, double* count,
+                          double* energy, void* stream);
+
 /* Flat, self-contained entry points on CANONICAL OIHW fp32 weights (SURVEY.md section 8(b)'s signatures): the weights are
  * packed into the caller's workspace on `stream`, then the fused kernel above runs.  For callers that do not keep
  * packed weights alive (one conv at a time from another framework); the training engine uses srk_conv3x3 directly.

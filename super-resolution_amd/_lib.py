@@ -21,7 +21,7 @@ EXPORTS = [
     "srk_sum_pool_fwd", "srk_sum_pool_bwd", "srk_workspace_bytes", "srk_conv3x3_fwd", "srk_conv3x3_dgrad", "srk_conv3x3_wgrad_flat",
     "srk_loss_workspace_bytes", "srk_sigmoid_fwd", "srk_sigmoid_bwd", "srk_lrelu_grad_mul", "srk_soft_count_fwd", "srk_soft_count_bwd",
     "srk_mask_l1_fwd", "srk_mask_l1_bwd", "srk_hitogram_fwd", "srk_hitogram_bwd", "srk_soft_hist_fwd", "srk_soft_hist_bwd",
-    "srk_jet_extract", "srk_strerror", "srk_version",
+    "srk_jet_extract", "srk_eval_image_stats", "srk_eval_pixel_counts", "srk_strerror", "srk_version",
     "srk_chain_recover", "srk_chain_stats", "srk_chain_epoch_plan", "srk_debug_chain_set", "srk_chain_set_wait_us", "srk_debug_chain_inject_fault",
     "srk_debug_hold_cus", "srk_debug_poison_lds", "srk_adam_count_step", "srk_debug_chain_inject_fault_async", "srk_debug_chain_skew",
 ]
@@ -64,6 +64,19 @@ class PackEntry(C.Structure):
         ("src", _fp), ("dst", _fp), ("src_cout", C.c_int32), ("src_cin", C.c_int32), ("transpose", C.c_int32),
         ("c_begin", C.c_int32), ("M", C.c_int32), ("k_off", C.c_int32), ("k_len", C.c_int32), ("K_total", C.c_int32),
         ("ps", C.c_int32), ("scale", C.c_float), ("fmt", C.c_int32), ("elem_begin", C.c_int64),
+    ]
+
+
+EVAL_MAX_K, EVAL_TIES, EVAL_MAX_FWM, EVAL_MAX_L = 64, 9, 16, 32
+EVAL_MAX, EVAL_MIN, EVAL_SUM, EVAL_NNZ, EVAL_NNZ_SUM, EVAL_NAN, EVAL_E, EVAL_PX, EVAL_PY, EVAL_PZ, EVAL_NSTAT = range(11)
+
+
+class EvalArgs(C.Structure):
+    _fields_ = [
+        ("x", _fp), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("sb", C.c_int64), ("sh", C.c_int64), ("sw", C.c_int64),
+        ("thr", C.c_float), ("K", C.c_int32), ("n_fwm", C.c_int32),
+        ("fwm_l", C.c_int32 * EVAL_MAX_FWM), ("fwm_j", C.c_int32 * EVAL_MAX_FWM),
+        ("stats", _fp), ("topv", _fp), ("topi", _fp), ("ties", _fp), ("fwm", _fp),
     ]
 
 
@@ -147,6 +160,8 @@ def lib():
         L.srk_conv3x3_wgrad_flat.argtypes = [_fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_int,
                                              C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, _fp, C.c_size_t, _fp]
         L.srk_jet_extract.argtypes = [_fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _fp, _fp]
+        L.srk_eval_image_stats.argtypes = [C.POINTER(EvalArgs), _fp]
+        L.srk_eval_pixel_counts.argtypes = [_fp, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_float, _fp, _fp, _fp]
         L.srk_loss_workspace_bytes.argtypes = [C.POINTER(C.c_size_t)]
         L.srk_sigmoid_fwd.argtypes = [_fp, _fp, C.c_long, C.c_float, C.c_float, _fp]
         L.srk_lrelu_grad_mul.argtypes = [_fp, _fp, _fp, C.c_long, C.c_float, _fp]
@@ -661,3 +676,42 @@ class AdamTable:
             return
         check(lib().srk_adam_step(self._dev.data_ptr(), self._n, self._total, lr, beta1, beta2, eps, weight_decay, step.data_ptr(),
                                   ptr(grad_scale), ptr(found_inf), stream_ptr()), "srk_adam_step")
+
+
+def _eval_view(x):
+    if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 1:
+        raise RuntimeError(f"srk_eval_*: expected a CUDA fp32 [B, 1, H, W] tensor, got {tuple(x.shape)} {x.dtype} on {x.device}")
+    return x.shape[0], x.shape[2], x.shape[3], x.stride(0), x.stride(2), x.stride(3)
+
+
+def eval_image_stats(x, thr, K, fwm_pairs, stats, topv, topi, ties, fwm):
+    """srk_eval_image_stats over the [B, 1, H, W] fp32 view ``x`` into the given record rows (stats [B, EVAL_NSTAT] fp64, topv [B, K]
+    fp32, topi [B, K] int32, ties [B, EVAL_TIES] int32, fwm [B, len(fwm_pairs)] fp64 or None), on the current stream."""
+    B, H, W, sb, sh, sw = _eval_view(x)
+    a = EvalArgs()
+    a.x, a.B, a.H, a.W, a.sb, a.sh, a.sw, a.thr, a.K = x.data_ptr(), B, H, W, sb, sh, sw, float(thr), int(K)
+    a.n_fwm = len(fwm_pairs)
+    if a.n_fwm > EVAL_MAX_FWM:
+        raise RuntimeError(f"srk_eval_image_stats: at most {EVAL_MAX_FWM} Fox-Wolfram moments per call, got {a.n_fwm}")
+    for p, (l, j) in enumerate(fwm_pairs):
+        a.fwm_l[p], a.fwm_j[p] = int(l), int(j)
+    for name, t, dt, cols in (("stats", stats, torch.float64, EVAL_NSTAT), ("topv", topv, torch.float32, K), ("topi", topi, torch.int32, K),
+                              ("ties", ties, torch.int32, EVAL_TIES), ("fwm", fwm, torch.float64, a.n_fwm)):
+        if t is None and cols == 0:
+            continue
+        if t is None or t.dtype != dt or tuple(t.shape) != (B, cols) or not t.is_contiguous() or t.device != x.device:
+            raise RuntimeError(f"srk_eval_image_stats: {name} must be a contiguous {dt} [{B}, {cols}] tensor on {x.device}")
+    a.stats, a.topv, a.topi, a.ties, a.fwm = stats.data_ptr(), topv.data_ptr(), topi.data_ptr(), ties.data_ptr(), ptr(fwm)
+    _poison()
+    check(lib().srk_eval_image_stats(C.byref(a), stream_ptr()), "srk_eval_image_stats")
+
+
+def eval_pixel_counts(x, thr, count, energy=None):
+    """srk_eval_pixel_counts: count[H, W] (+ energy[H, W]) fp64 += the per-pixel counts of x > thr over the batch (see srk.h)."""
+    B, H, W, sb, sh, sw = _eval_view(x)
+    for t in (count, energy):
+        if t is not None and (t.dtype != torch.float64 or tuple(t.shape) != (H, W) or not t.is_contiguous() or t.device != x.device):
+            raise RuntimeError(f"srk_eval_pixel_counts: maps must be contiguous float64 [{H}, {W}] tensors on {x.device}")
+    _poison()
+    check(lib().srk_eval_pixel_counts(x.data_ptr(), B, H, W, sb, sh, sw, float(thr), count.data_ptr(), ptr(energy), stream_ptr()),
+          "srk_eval_pixel_counts")
