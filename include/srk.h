@@ -403,6 +403,22 @@ int srk_conv3x3_wgrad_flat(const void* x, int ldc_in, int c_in_off, int Cin, con
                            int pixel_shuffle_r, int dtype, void* workspace, size_t ws_bytes, void* stream);
 /* (srk_conv3x3_wgrad / srk_conv3x3_wgrad_batched above are the struct forms the engine uses: packed dense-block batches) */
 
+/* nn.ConvTranspose2d(Cin, Cout, kernel_size=2, stride=2, padding=0): the generator's transposed-conv upsampling stages
+ * (--use_transposed_conv / --fully_transposed_conv, models.py:69-83), and its autograd gradients.  Dense contiguous NCHW fp32:
+ * x [N,Cin,H,W], y / dy [N,Cout,2H,2W]; w and dw in PyTorch's [Cin,Cout,2,2] layout; bias / db [Cout] (may be NULL).  fp32
+ * MFMAs, fp32 accumulation.
+ *   fwd:   y[n,co,2i+a,2j+b] = lrelu_slope(bias[co] + sum_ci x[n,ci,i,j] w[ci,co,a,b]); slope 1 = no activation.  y 8-byte aligned.
+ *   dgrad: dx[n,ci,i,j] = sum_{co,a,b} dy[n,co,2i+a,2j+b] w[ci,co,a,b]  (H, W = extent of x).
+ *   wgrad: dw[ci,co,a,b] = scale * sum_{n,i,j} x[n,ci,i,j] dy[n,co,2i+a,2j+b] (+ dw if accumulate), db[co] likewise from sum dy.
+ *          Workspace: srk_workspace_bytes(SRK_OP_TCONV2X2_WGRAD, N, H, W, Cin, Cout, 0, &bytes).  Deterministic (split over the
+ *          pixels, partial sums added in a fixed order, no float atomics). */
+enum { SRK_OP_TCONV2X2_WGRAD = 3 };
+int srk_tconv2x2_fwd(const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int Cin, int Cout,
+                     float lrelu_slope, void* stream);
+int srk_tconv2x2_dgrad(const float* dy, const float* w, float* dx, int N, int H, int W, int Cin, int Cout, void* stream);
+int srk_tconv2x2_wgrad(const float* x, const float* dy, float* dw, float* db, int N, int H, int W, int Cin, int Cout, float scale,
+                       int accumulate, void* workspace, size_t ws_bytes, void* stream);
+
 /* torch.optim.Adam.step() of a whole parameter list in ONE launch (esrgan.py:299,305,487,623: the generator's and the discriminators'
  * optimizers): fp32 parameters, gradients, exp_avg, exp_avg_sq behind a device table of pointers.  Arithmetic of ATen's fused Adam
  * (amsgrad off, maximize off): g /= *grad_scale (if given); g += weight_decay * p; exp_avg = lerp(exp_avg, g, 1 - beta1);

@@ -7,7 +7,7 @@ Import by string (the directory name carries a hyphen)::
 """
 from . import _lib, ops, engine, models, evaluation, observables, losses, datasets  # noqa: F401
 from .models import (GeneratorRRDB, Markovian_Discriminator, Standard_Discriminator, Conditional_Discriminator, SumPool2d, DenseResidualBlock,  # noqa: F401
-                     ResidualInResidualDenseBlock, Conv3x3, discriminator_block, weight_reset, uniform_reset)
+                     ResidualInResidualDenseBlock, Conv3x3, ConvTranspose2x2, discriminator_block, weight_reset, uniform_reset)
 
 __all__ = ["models", "ops", "engine", "_lib", "losses", "datasets", "evaluation", "observables", "GeneratorRRDB", "Markovian_Discriminator", "Standard_Discriminator", "Conditional_Discriminator", "SumPool2d",
-           "DenseResidualBlock", "ResidualInResidualDenseBlock", "Conv3x3", "discriminator_block", "weight_reset", "uniform_reset"]
+           "DenseResidualBlock", "ResidualInResidualDenseBlock", "Conv3x3", "ConvTranspose2x2", "discriminator_block", "weight_reset", "uniform_reset"]

@@ -24,9 +24,11 @@ EXPORTS = [
     "srk_jet_extract", "srk_eval_image_stats", "srk_eval_pixel_counts", "srk_strerror", "srk_version",
     "srk_chain_recover", "srk_chain_stats", "srk_chain_epoch_plan", "srk_debug_chain_set", "srk_chain_set_wait_us", "srk_debug_chain_inject_fault",
     "srk_debug_hold_cus", "srk_debug_poison_lds", "srk_adam_count_step", "srk_debug_chain_inject_fault_async", "srk_debug_chain_skew",
+    "srk_tconv2x2_fwd", "srk_tconv2x2_dgrad", "srk_tconv2x2_wgrad",
 ]
 ERR_CHAIN_TIMEOUT = -6
 OP_CONV_FWD, OP_CONV_DGRAD, OP_CONV_WGRAD = 0, 1, 2
+OP_TCONV2X2_WGRAD = 3
 
 _fp = C.c_void_p
 
@@ -159,6 +161,10 @@ def lib():
                                         C.c_int, C.c_int, C.c_int, _fp, C.c_size_t, _fp]
         L.srk_conv3x3_wgrad_flat.argtypes = [_fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_int,
                                              C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, _fp, C.c_size_t, _fp]
+        L.srk_tconv2x2_fwd.argtypes = [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _fp]
+        L.srk_tconv2x2_dgrad.argtypes = [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp]
+        L.srk_tconv2x2_wgrad.argtypes = [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _fp,
+                                         C.c_size_t, _fp]
         L.srk_jet_extract.argtypes = [_fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _fp, _fp]
         L.srk_eval_image_stats.argtypes = [C.POINTER(EvalArgs), _fp]
         L.srk_eval_pixel_counts.argtypes = [_fp, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_float, _fp, _fp, _fp]
@@ -550,6 +556,49 @@ def conv3x3_wgrad_flat(x: "View", dy: "View", dw, db, *, N, H, W, Cin, Cout, str
     check(lib().srk_conv3x3_wgrad_flat(x.t.data_ptr(), x.ldc, x.coff, Cin, dy.t.data_ptr(), dy.ldc, dy.coff, Cout, dw.data_ptr(), ptr(db),
                                        N, H, W, stride, scale, int(accumulate), ps, 0, ws.data_ptr(), ws.numel(), stream_ptr()),
           "srk_conv3x3_wgrad_flat")
+
+
+def _tconv_args(x, *ts):
+    """(N, H, W) of a ConvTranspose2d(k=2, s=2) call on the input extent of x; every tensor a contiguous fp32 GPU tensor"""
+    for t in (x,) + ts:
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise RuntimeError("super-resolution_amd: srk_tconv2x2_* take contiguous fp32 ROCm GPU tensors (no CPU fallback)")
+    return x.shape[0], x.shape[2], x.shape[3]
+
+
+def tconv2x2_fwd_flat(x, w, bias, y, *, slope=1.0):
+    """srk_tconv2x2_fwd: y [N,Cout,2H,2W] = ConvTranspose2d(k=2, s=2)(x [N,Cin,H,W]) with w [Cin,Cout,2,2], then LeakyReLU(slope)
+    (slope 1: none)."""
+    N, H, W = _tconv_args(x, w, bias, y)
+    Cin, Cout = w.shape[0], w.shape[1]
+    if tuple(x.shape) != (N, Cin, H, W) or tuple(y.shape) != (N, Cout, 2 * H, 2 * W) or tuple(w.shape[2:]) != (2, 2):
+        raise ValueError(f"tconv2x2_fwd: x {tuple(x.shape)}, w {tuple(w.shape)}, y {tuple(y.shape)} do not fit")
+    _poison()
+    check(lib().srk_tconv2x2_fwd(x.data_ptr(), w.data_ptr(), ptr(bias), y.data_ptr(), N, H, W, Cin, Cout, float(slope), stream_ptr()),
+          "srk_tconv2x2_fwd")
+
+
+def tconv2x2_dgrad_flat(dy, w, dx):
+    """srk_tconv2x2_dgrad: dx [N,Cin,H,W] from dy [N,Cout,2H,2W]."""
+    N, H, W = _tconv_args(dx, dy, w)
+    Cin, Cout = w.shape[0], w.shape[1]
+    if tuple(dx.shape) != (N, Cin, H, W) or tuple(dy.shape) != (N, Cout, 2 * H, 2 * W) or tuple(w.shape[2:]) != (2, 2):
+        raise ValueError(f"tconv2x2_dgrad: dy {tuple(dy.shape)}, w {tuple(w.shape)}, dx {tuple(dx.shape)} do not fit")
+    _poison()
+    check(lib().srk_tconv2x2_dgrad(dy.data_ptr(), w.data_ptr(), dx.data_ptr(), N, H, W, Cin, Cout, stream_ptr()), "srk_tconv2x2_dgrad")
+
+
+def tconv2x2_wgrad_flat(x, dy, dw, db, *, scale=1.0, accumulate=False):
+    """srk_tconv2x2_wgrad: dw [Cin,Cout,2,2] (and db [Cout], may be None) = scale * sum (+ the old values if accumulate)."""
+    N, H, W = _tconv_args(x, dy, dw, db)
+    Cin, Cout = dw.shape[0], dw.shape[1]
+    if tuple(x.shape) != (N, Cin, H, W) or tuple(dy.shape) != (N, Cout, 2 * H, 2 * W) or tuple(dw.shape[2:]) != (2, 2) or \
+            (db is not None and tuple(db.shape) != (Cout,)):
+        raise ValueError(f"tconv2x2_wgrad: x {tuple(x.shape)}, dy {tuple(dy.shape)}, dw {tuple(dw.shape)} do not fit")
+    ws = _workspace(workspace_bytes(OP_TCONV2X2_WGRAD, N, H, W, Cin, Cout), x.device)
+    _poison()
+    check(lib().srk_tconv2x2_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), ptr(db), N, H, W, Cin, Cout, float(scale), int(accumulate),
+                                   ws.data_ptr(), ws.numel(), stream_ptr()), "srk_tconv2x2_wgrad")
 
 
 def loss_workspace(device) -> torch.Tensor:

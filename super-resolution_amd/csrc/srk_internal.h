@@ -20,3 +20,6 @@ static inline int srk_div_up(int v, int m) { return (v + m - 1) / m; }
     if (e__ != hipSuccess) return SRK_ERR_LAUNCH;            \
   } while (0)
 
+
+// srk_tconv.hip: workspace of srk_tconv2x2_wgrad (srk_workspace_bytes(SRK_OP_TCONV2X2_WGRAD, ...))
+size_t srk_tconv2x2_wgrad_ws_bytes(int N, int H, int W, int Cin, int Cout);

@@ -403,6 +403,7 @@ extern "C" int srk_workspace_bytes(int op, int N, int H, int W, int Cin, int Cou
       *out = best;
       return SRK_OK;
     }
+    case SRK_OP_TCONV2X2_WGRAD: *out = srk_tconv2x2_wgrad_ws_bytes(N, H, W, Cin, Cout); return SRK_OK;
     default: return SRK_ERR_BAD_ARG;
   }
 }

@@ -35,6 +35,28 @@ class Conv3x3(nn.Conv2d):
         return ops.to_nchw(y)
 
 
+class ConvTranspose2x2(nn.ConvTranspose2d):
+    """``nn.ConvTranspose2d(cin, cout, 2, stride=2)`` whose forward and gradients are the srk_tconv2x2 kernels (NCHW in / NCHW out,
+    twice differentiable).  Same parameters, ``state_dict`` keys and ``isinstance`` behaviour as the PyTorch module it replaces
+    in the generator's transposed-conv upsampling stages (models.py:69-83); every other geometry raises."""
+
+    def __init__(self, in_channels, out_channels, kernel_size=2, stride=2, padding=0, output_padding=0, groups=1, bias=True,
+                 dilation=1, padding_mode="zeros", device=None, dtype=None):
+        def pair(v):
+            return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+        if (pair(kernel_size) != (2, 2) or pair(stride) != (2, 2) or pair(padding) != (0, 0) or pair(output_padding) != (0, 0)
+                or groups != 1 or pair(dilation) != (1, 1) or padding_mode != "zeros"):
+            raise NotImplementedError("only the reference's ConvTranspose2d(kernel_size=2, stride=2, padding=0) is implemented")
+        super().__init__(in_channels, out_channels, 2, stride=2, padding=0, bias=bias, device=device, dtype=dtype)
+
+    def forward(self, x, output_size=None):
+        if output_size is not None and tuple(output_size)[-2:] != (2 * x.shape[-2], 2 * x.shape[-1]):
+            raise NotImplementedError("ConvTranspose2x2: output_size must be twice the input extent")
+        if x.dim() != 4:
+            raise NotImplementedError("ConvTranspose2x2: batched [N, C, H, W] input expected")
+        return ops.tconv2x2(x.float(), self.weight, self.bias)
+
+
 class DenseResidualBlock(nn.Module):
     """models.py:9-41.  Parameter container; GeneratorRRDB runs it concat-free (engine.py) unless drop_rate > 0, where the
     module-wise forward below is used (HIP convolutions, torch.cat / Dropout2d glue: a non-default branch)."""
@@ -100,9 +122,9 @@ class GeneratorRRDB(nn.Module):
         self.conv2 = Conv3x3(filters, filters, kernel_size=3, stride=1, padding=1)
         # Upsampling stages (models.py:69-90).  Default: conv F->4F + LeakyReLU + PixelShuffle(2), fused into the HIP engine.
         # The two non-default variants put a ConvTranspose2d(F, F, 2, stride 2) + LeakyReLU at every odd stage
-        # (use_transposed_conv) or at every stage (fully_tconv_upsample): those layers are plain PyTorch modules (SURVEY 8b:
-        # non-default branches may stay on PyTorch ops) and the generator then runs module by module, every 3x3 conv still
-        # on the HIP kernels, so checkpoints trained with these flags load and run.
+        # (use_transposed_conv) or at every stage (fully_tconv_upsample): those layers are ConvTranspose2x2 modules (the
+        # srk_tconv2x2 kernels, same parameters and keys as nn.ConvTranspose2d) and the generator then runs module by module,
+        # every 3x3 conv on the HIP kernels too, so checkpoints trained with these flags load and run.
         kinds = ["tconv" if (fully_tconv_upsample and not use_transposed_conv) or (use_transposed_conv and u % 2 == 1) else "shuffle"
                  for u in range(num_upsample)]
         upsample_layers = []
@@ -111,7 +133,7 @@ class GeneratorRRDB(nn.Module):
                 upsample_layers += [Conv3x3(filters, filters * 4, kernel_size=3, stride=1, padding=1), nn.LeakyReLU(),
                                     nn.PixelShuffle(upscale_factor=2)]
             else:
-                upsample_layers += [nn.ConvTranspose2d(filters, filters, kernel_size=2, stride=2, padding=0), nn.LeakyReLU()]
+                upsample_layers += [ConvTranspose2x2(filters, filters, kernel_size=2, stride=2, padding=0), nn.LeakyReLU()]
         self.upsampling = nn.Sequential(*upsample_layers)
         self.modulewise = drop_rate > 0 or "tconv" in kinds      # these run _forward_modulewise instead of the fused engine
         if num_final_layer_res > 0:

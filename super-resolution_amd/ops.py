@@ -401,3 +401,99 @@ class _SumPool(torch.autograd.Function):
 
 def sum_pool(x, k):
     return _SumPool.apply(x, k)
+
+
+# nn.ConvTranspose2d(k=2, s=2) on srk_tconv.hip (NCHW).  The three nodes are closed under differentiation like ConvPre / ConvDgrad /
+# ConvWgrad: the forward's input gradient is the dgrad kernel, the dgrad's is the forward kernel (no bias), and the weight gradient's
+# gradients are a dgrad (w.r.t. x) and a forward (w.r.t. dy, the bias gradient's gradient as the bias).
+def _tconv_fwd_raw(x, w, b):
+    _require_gpu(x)
+    y = torch.empty(x.shape[0], w.shape[1], 2 * x.shape[2], 2 * x.shape[3], dtype=torch.float32, device=x.device)
+    L.tconv2x2_fwd_flat(x, w.detach().contiguous(), None if b is None else b.detach().contiguous(), y)
+    return y
+
+
+class TConvFwd(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, b):
+        _require_gpu(x)
+        x = x.contiguous()
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(x, w)
+        ctx.has_b = b is not None
+        ctx.want_pg = _want_param_grads()
+        return _tconv_fwd_raw(x, w, b)
+
+    @staticmethod
+    def backward(ctx, dy):
+        if dy is None:
+            return None, None, None
+        x, w = ctx.saved_tensors
+        dy = dy.contiguous()
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = TConvDgrad.apply(dy, w)
+        if ctx.want_pg and (ctx.needs_input_grad[1] or (ctx.has_b and ctx.needs_input_grad[2])):
+            dw, db = TConvWgrad.apply(x, dy)
+            if not ctx.has_b:
+                db = None
+        return dx, dw, db
+
+
+class TConvDgrad(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, dy, w):
+        _require_gpu(dy)
+        dy = dy.contiguous()
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(dy, w)
+        dx = torch.empty(dy.shape[0], w.shape[0], dy.shape[2] // 2, dy.shape[3] // 2, dtype=torch.float32, device=dy.device)
+        L.tconv2x2_dgrad_flat(dy, w.detach().contiguous(), dx)
+        return dx
+
+    @staticmethod
+    def backward(ctx, gdx):
+        if gdx is None:
+            return None, None
+        dy, w = ctx.saved_tensors
+        gdx = gdx.contiguous()
+        g_dy = g_w = None
+        if ctx.needs_input_grad[0]:
+            g_dy = TConvFwd.apply(gdx, w, None)
+        if ctx.needs_input_grad[1]:
+            g_w, _ = TConvWgrad.apply(gdx, dy)
+        return g_dy, g_w
+
+
+class TConvWgrad(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, dy):
+        _require_gpu(x)
+        x, dy = x.contiguous(), dy.contiguous()
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(x, dy)
+        Cin, Cout = x.shape[1], dy.shape[1]
+        dw = torch.empty(Cin, Cout, 2, 2, dtype=torch.float32, device=x.device)
+        db = torch.empty(Cout, dtype=torch.float32, device=x.device)
+        L.tconv2x2_wgrad_flat(x, dy, dw, db)
+        return dw, db
+
+    @staticmethod
+    def backward(ctx, ggw, ggb):
+        if ggw is None and ggb is None:
+            return None, None
+        x, dy = ctx.saved_tensors
+        g_x = g_dy = None
+        if ctx.needs_input_grad[0] and ggw is not None:
+            g_x = TConvDgrad.apply(dy, ggw)
+        if ctx.needs_input_grad[1]:
+            if ggw is not None:
+                g_dy = TConvFwd.apply(x, ggw, ggb)
+            else:
+                g_dy = ggb.view(1, -1, 1, 1).expand_as(dy)
+        return g_x, g_dy
+
+
+def tconv2x2(x, w, b=None):
+    """nn.functional.conv_transpose2d(x, w, b, stride=2) with w [Cin, Cout, 2, 2] on an NCHW fp32 GPU tensor; differentiable twice."""
+    return TConvFwd.apply(x, w, b)
