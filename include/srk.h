@@ -419,6 +419,37 @@ int srk_tconv2x2_dgrad(const float* dy, const float* w, float* dx, int N, int H,
 int srk_tconv2x2_wgrad(const float* x, const float* dy, float* dw, float* db, int N, int H, int W, int Cin, int Cout, float scale,
                        int accumulate, void* workspace, size_t ws_bytes, void* stream);
 
+/* Sinkhorn Wasserstein loss head (esrgan.py:321,539-542: SinkhornDistance(eps, 100, 'sum')(cut_smaller(sort(gen))[..., None],
+ * cut_smaller(sort(real))[..., None]); utils.py:147-257) with an implicit cost matrix C_ij = (x_i - y_j)^2: nothing N'xM' is stored.
+ * fp32, contiguous, rows of `cap` floats per image; the point counts n[0] = N', n[1] = M' (1 <= n <= cap) live on the DEVICE.
+ * Every reduction runs in a fixed order: repeated calls are bit-identical.  No call synchronises with the host.
+ *   sort_cut:  per image b of t [B][P] (P <= SRK_SORT_CUT_MAX): *n_out = max over the batch of #{t > threshold}, or P if that is 0
+ *              (cut_smaller, utils.py:239-257); vals[b][0..n) = the last n entries of the image's ascending stable sort (NaN last,
+ *              -0 == +0, ties by the lower flat index first), idx = their flat indices.  vals / idx [B][P].
+ *   fwd:       max_iter log-domain iterations from u = v = 0 with a = log(1/N' + 1e-8), b = log(1/M' + 1e-8):
+ *              u_i += eps (a - LSE_j M_ij), then v_j += eps (b - LSE_i M_ij), M_ij = (-C_ij + u_i + v_j) / eps;
+ *              err_k = mean_b sum_i |du_i|; after the first k with err_k < 0.1 the remaining launches are no-ops (state[1] = 1).
+ *              state[0] = K (iterations run).  u [B][cap_x], v [B][cap_y] end as u^K, v^K.  hist_L [max_iter][B][cap_x],
+ *              hist_R [max_iter][B][cap_y]: every iteration's row / column LSE (log2 units) for the backward.  work: B (cap_x + cap_y).
+ *              err [max_iter] (may be NULL): err_k for k <= K.  cost [B] = sum_ij pi_ij C_ij, pi = exp(M(u^K, v^K)) (formed as exp(M(u^K, v^{K-1}) - R^K + b)).
+ *   bwd:       gradient of sum_b g_cost[b] cost[b] through all K unrolled iterations: gx [B][cap_x], gy [B][cap_y] (gy may be NULL);
+ *              work: 3 B cap_x + 2 B cap_y floats.  The other arguments are those of (and written by) the forward; u^k, v^k are replayed bit-exactly from the history.
+ *   plan:      pi and C [B][n_x][n_y] materialised from host-known n_x, n_y and the forward's u, v (rows of n_x / n_y floats).
+ *   scatter_rows: out [B][P] = 0, then out[b][idx[b][p]] = g[b][p] for p < *n (g, idx [B][P]: the sort_cut layout). */
+/* Costs: sort_cut ranks by counting, O(P^2) compares per image (fine at 80^2; ~4e9 per image at P = 65536, not measured there).
+ * bwd replays u^k, v^k from u^0 = v^0 = 0 at every reverse step: O(K^2 B (N' + M')) reads of the history, beside the O(K B N' M')
+ * pair work. */
+enum { SRK_SORT_CUT_MAX = 65536 };
+int srk_sort_cut(const float* t, int B, int P, float threshold, float* vals, int* idx, int* n_out, void* stream);
+int srk_sinkhorn_fwd(const float* x, const float* y, const int* n, int B, int cap_x, int cap_y, float eps, int max_iter, float* u,
+                     float* v, float* hist_L, float* hist_R, float* work, int* state, float* err, float* cost, void* stream);
+int srk_sinkhorn_bwd(const float* x, const float* y, const int* n, int B, int cap_x, int cap_y, float eps, int max_iter,
+                     const float* hist_L, const float* hist_R, const int* state, const float* g_cost, float* gx, float* gy, float* work,
+                     void* stream);
+int srk_sinkhorn_plan(const float* x, const float* y, const float* u, const float* v, int B, int n_x, int n_y, float eps, float* pi,
+                      float* cost_matrix, void* stream);
+int srk_scatter_rows(const float* g, const int* idx, const int* n, int B, int P, float* out, void* stream);
+
 /* torch.optim.Adam.step() of a whole parameter list in ONE launch (esrgan.py:299,305,487,623: the generator's and the discriminators'
  * optimizers): fp32 parameters, gradients, exp_avg, exp_avg_sq behind a device table of pointers.  Arithmetic of ATen's fused Adam
  * (amsgrad off, maximize off): g /= *grad_scale (if given); g += weight_decay * p; exp_avg = lerp(exp_avg, g, 1 - beta1);

@@ -25,7 +25,9 @@ EXPORTS = [
     "srk_chain_recover", "srk_chain_stats", "srk_chain_epoch_plan", "srk_debug_chain_set", "srk_chain_set_wait_us", "srk_debug_chain_inject_fault",
     "srk_debug_hold_cus", "srk_debug_poison_lds", "srk_adam_count_step", "srk_debug_chain_inject_fault_async", "srk_debug_chain_skew",
     "srk_tconv2x2_fwd", "srk_tconv2x2_dgrad", "srk_tconv2x2_wgrad",
+    "srk_sort_cut", "srk_sinkhorn_fwd", "srk_sinkhorn_bwd", "srk_sinkhorn_plan", "srk_scatter_rows",
 ]
+SORT_CUT_MAX = 65536
 ERR_CHAIN_TIMEOUT = -6
 OP_CONV_FWD, OP_CONV_DGRAD, OP_CONV_WGRAD = 0, 1, 2
 OP_TCONV2X2_WGRAD = 3
@@ -165,6 +167,11 @@ def lib():
         L.srk_tconv2x2_dgrad.argtypes = [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp]
         L.srk_tconv2x2_wgrad.argtypes = [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _fp,
                                          C.c_size_t, _fp]
+        L.srk_sort_cut.argtypes = [_fp, C.c_int, C.c_int, C.c_float, _fp, _fp, _fp, _fp]
+        L.srk_sinkhorn_fwd.argtypes = [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int] + [_fp] * 9
+        L.srk_sinkhorn_bwd.argtypes = [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int] + [_fp] * 8
+        L.srk_sinkhorn_plan.argtypes = [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_float, _fp, _fp, _fp]
+        L.srk_scatter_rows.argtypes = [_fp, _fp, _fp, C.c_int, C.c_int, _fp, _fp]
         L.srk_jet_extract.argtypes = [_fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _fp, _fp]
         L.srk_eval_image_stats.argtypes = [C.POINTER(EvalArgs), _fp]
         L.srk_eval_pixel_counts.argtypes = [_fp, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_float, _fp, _fp, _fp]
@@ -764,3 +771,72 @@ def eval_pixel_counts(x, thr, count, energy=None):
     _poison()
     check(lib().srk_eval_pixel_counts(x.data_ptr(), B, H, W, sb, sh, sw, float(thr), count.data_ptr(), ptr(energy), stream_ptr()),
           "srk_eval_pixel_counts")
+
+
+# ---- Sinkhorn loss head (srk_sinkhorn.hip).  Every buffer is a fresh tensor of the caching allocator on the current stream: two
+# views running on two streams never share scratch.
+def sort_cut(t, n, slot, threshold=0.0):
+    """srk_sort_cut: t [B, P] -> (vals [B, P], idx int32 [B, P]); n[slot] (int32, on the device) = N', and vals[:, :N'] is the tail
+    of the ascending stable sort that cut_smaller keeps, idx their flat indices."""
+    B, P = t.shape
+    vals = torch.empty(B, P, dtype=torch.float32, device=t.device)
+    idx = torch.empty(B, P, dtype=torch.int32, device=t.device)
+    _poison()
+    check(lib().srk_sort_cut(t.data_ptr(), B, P, float(threshold), vals.data_ptr(), idx.data_ptr(), n.data_ptr() + 4 * slot, stream_ptr()),
+          "srk_sort_cut")
+    return vals, idx
+
+
+def sinkhorn_fwd(x, y, n, eps, max_iter, want_err=False):
+    """srk_sinkhorn_fwd on x [B, cap_x], y [B, cap_y] with n = (N', M') on the device.  Returns (cost [B], saved dict)."""
+    B, cx = x.shape
+    cy = y.shape[1]
+    f = dict(dtype=torch.float32, device=x.device)
+    u, v = torch.empty(B, cx, **f), torch.empty(B, cy, **f)
+    hL, hR = torch.empty(max_iter, B, cx, **f), torch.empty(max_iter, B, cy, **f)
+    work = torch.empty(B * (cx + cy), **f)
+    state = torch.empty(2, dtype=torch.int32, device=x.device)
+    err = torch.full((max_iter,), float("nan"), **f) if want_err else None
+    cost = torch.empty(B, **f)
+    _poison()
+    check(lib().srk_sinkhorn_fwd(x.data_ptr(), y.data_ptr(), n.data_ptr(), B, cx, cy, float(eps), int(max_iter), u.data_ptr(), v.data_ptr(),
+                                 hL.data_ptr(), hR.data_ptr(), work.data_ptr(), state.data_ptr(), ptr(err), cost.data_ptr(), stream_ptr()),
+          "srk_sinkhorn_fwd")
+    return cost, dict(u=u, v=v, hL=hL, hR=hR, state=state, err=err)
+
+
+def sinkhorn_bwd(x, y, n, eps, max_iter, saved, g_cost, want_gy=True):
+    """srk_sinkhorn_bwd: (gx [B, cap_x], gy [B, cap_y] or None) of sum_b g_cost[b] cost[b]."""
+    B, cx = x.shape
+    cy = y.shape[1]
+    f = dict(dtype=torch.float32, device=x.device)
+    gx = torch.empty(B, cx, **f)
+    gy = torch.empty(B, cy, **f) if want_gy else None
+    work = torch.empty(3 * B * cx + 2 * B * cy, **f)
+    g_cost = g_cost.contiguous().float()
+    _poison()
+    check(lib().srk_sinkhorn_bwd(x.data_ptr(), y.data_ptr(), n.data_ptr(), B, cx, cy, float(eps), int(max_iter),
+                                 saved["hL"].data_ptr(), saved["hR"].data_ptr(), saved["state"].data_ptr(),
+                                 g_cost.data_ptr(), gx.data_ptr(), ptr(gy), work.data_ptr(), stream_ptr()), "srk_sinkhorn_bwd")
+    return gx, gy
+
+
+def sinkhorn_plan(x, y, u, v, eps):
+    """srk_sinkhorn_plan: (pi, C) [B, N, M] for host-known N = x.shape[1], M = y.shape[1]."""
+    B, nx = x.shape
+    ny = y.shape[1]
+    pi = torch.empty(B, nx, ny, dtype=torch.float32, device=x.device)
+    cm = torch.empty_like(pi)
+    _poison()
+    check(lib().srk_sinkhorn_plan(x.data_ptr(), y.data_ptr(), u.data_ptr(), v.data_ptr(), B, nx, ny, float(eps), pi.data_ptr(), cm.data_ptr(),
+                                  stream_ptr()), "srk_sinkhorn_plan")
+    return pi, cm
+
+
+def scatter_rows(g, idx, n):
+    """srk_scatter_rows: out [B, P] = 0, out[b, idx[b, p]] = g[b, p] for p < n[0]."""
+    B, P = g.shape
+    out = torch.empty(B, P, dtype=torch.float32, device=g.device)
+    _poison()
+    check(lib().srk_scatter_rows(g.data_ptr(), idx.data_ptr(), n.data_ptr(), B, P, out.data_ptr(), stream_ptr()), "srk_scatter_rows")
+    return out

@@ -7,7 +7,8 @@ working.  The iteration itself is ``train.Stepper`` (HIP kernels, optional data 
 heads ``--lambda_nnz/mask/hit/hist`` (fused kernels, losses.py), ``--conditional`` and ``--discriminator standard``.  Outside
 this build's scope and therefore raising instead of silently training something else: ``--lambda_wasser``,
 the Wasserstein critics, validation/evaluation plots and the HDF5 / text event readers (the jet datasets take ``.npy`` row
-tables).
+tables).  The Wasserstein loss head itself exists one layer down: ``train.Stepper(lambda_wasser=..., sinkhorn_eps=...)`` and
+``losses.wasser_loss`` / ``losses.SinkhornDistance`` (csrc/srk_sinkhorn.hip); only this entry point does not switch it on yet.
 
 Multi-GPU: launch one process per GPU, e.g.
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m super-resolution_amd.esrgan ...

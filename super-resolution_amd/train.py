@@ -90,7 +90,7 @@ class Stepper:
                  lambda_hr=1.0, lambda_adv=0.01, lambda_lr=0.1, lambda_reg=0.01, d_threshold=0.001, scaling_power=1.0,
                  exact_dp=True, hr_shape=None, lr_g=0.0, lr_d=0.0, weight_decay=0.0, multiplier=1.0, num_final_layer_res=0,
                  uniform_init=False, lambda_nnz=0.0, lambda_mask=0.0, lambda_hit=0.0, lambda_hist=0.0, hit_threshold=0.5, sigma=500.0, conditional=False, drop_rate=0.0, discriminator="patch", relativistic=True,
-                 use_transposed_conv=False, fully_tconv_upsample=False):
+                 use_transposed_conv=False, fully_tconv_upsample=False, lambda_wasser=0.0, sinkhorn_eps=0.1):
         self.workload = workload
         self.drop_rate = drop_rate
         self.relativistic = relativistic
@@ -98,6 +98,8 @@ class Stepper:
         # optional physics heads of the G phase (esrgan.py:522-547); the histogram head needs set_hist_binedges() first
         self.lambda_nnz, self.lambda_mask, self.lambda_hit, self.lambda_hist = lambda_nnz, lambda_mask, lambda_hit, lambda_hist
         self.hit_threshold, self.sigma = hit_threshold, sigma
+        # Sinkhorn Wasserstein head (esrgan.py:321,539-542): SinkhornDistance(sinkhorn_eps, 100, 'sum') on the device (losses.wasser_loss)
+        self.lambda_wasser, self.sinkhorn_eps = lambda_wasser, sinkhorn_eps
         self.histograms, self.criterion_hist = {}, {}
         self.device = device
         self.distributed = distributed
@@ -254,14 +256,14 @@ class Stepper:
         vec = torch.stack([d.get(0, z).reshape(()), d.get(1, z).reshape(()), out["g_loss"].reshape(()), g(0, "tot"), g(1, "tot"),
                            g(0, "adv"), g(1, "adv"), g(0, "pixel"), g(1, "pixel"), g(0, "lr"), g(1, "lr"),
                            g(0, "hist"), g(1, "hist"), g(0, "nnz"), g(1, "nnz"), g(0, "mask"), g(1, "mask"),
-                           g(0, "hit"), g(1, "hit"),
+                           g(0, "hit"), g(1, "hit"), g(0, "wasser"), g(1, "wasser"),
                            (out["nan_probe"].reshape(()) if out.get("nan_probe") is not None else z)]).tolist()
         names = ['d_loss_def', 'd_loss_pow', 'g_loss', 'def_loss', 'pow_loss', 'adv_loss', 'adv_loss_pow', 'pixel_loss',
                  'pixel_loss_pow', 'lr_loss', 'lr_loss_pow', 'hist_loss', 'hist_loss_pow', 'nnz_loss', 'nnz_loss_pow',
-                 'mask_loss', 'mask_loss_pow', 'hit_loss', 'hit_loss_pow']
+                 'mask_loss', 'mask_loss_pow', 'hit_loss', 'hit_loss_pow', 'wasser_loss', 'wasser_loss_pow']
         out_d = dict(zip(names, vec))
         out_d["nan_probe"] = vec[-1]       # data parallel: sum of all ranks' losses (NaN on every rank if any rank's is); else 0
-        for name in ('wasser_loss', 'wasser_loss_pow', 'wasser_dist', 'wasser_dist_pow'):   # heads this build does not implement
+        for name in ('wasser_dist', 'wasser_dist_pow'):     # the Wasserstein critic (--wasserstein): not implemented
             out_d[name] = 0.0
         return out_d
 
@@ -333,7 +335,8 @@ class Stepper:
                 tot = self.lambda_hr * loss_pixel + self.lambda_adv * loss_GAN + self.lambda_lr * loss_lr_pixel
                 parts[k] = dict(pixel=loss_pixel.detach(), lr=loss_lr_pixel.detach(), adv=loss_GAN.detach())
                 # optional physics heads: one fused HIP pass each (csrc/srk_loss.hip) instead of 3-6 HR-sized ATen ops.
-                # Under data parallelism these are per-rank means of per-rank batches (like the reference under DDP would be).
+                # Under data parallelism these are per-rank means of per-rank batches (like the reference under DDP would be); the
+                # Wasserstein head likewise cuts and transports each rank's shard on its own.
                 if self.lambda_nnz > 0:                                                    # esrgan.py:522-525
                     loss_nnz = self.mse(losses.soft_count(generated[k], 0.0, 50000.0), losses.hard_count(ground_truth[k], 0.0))
                     tot = tot + self.lambda_nnz * loss_nnz
@@ -350,6 +353,10 @@ class Stepper:
                     loss_hist = self.criterion_hist[k](gen_hist, real_hist)
                     tot = tot + self.lambda_hist * loss_hist
                     parts[k]["hist"] = loss_hist.detach()
+                if self.lambda_wasser > 0:                                                 # esrgan.py:539-542
+                    loss_wasser = losses.wasser_loss(generated[k], ground_truth[k].detach(), self.sinkhorn_eps)
+                    tot = tot + self.lambda_wasser * loss_wasser
+                    parts[k]["wasser"] = loss_wasser.detach()
                 if self.lambda_hit > 0:                                                    # esrgan.py:543-547
                     gen_hit = losses.get_hitogram(generated[k], self.factor, self.hit_threshold, self.sigma)
                     target = losses.get_hitogram(ground_truth[k], self.factor, self.hit_threshold, self.sigma)
