@@ -114,6 +114,11 @@ size_t srk_conv3x3_seq_signs_bytes(const srk_conv_args* args, int n);
 /* layout tag of those bits (tile rows | wp_format << 8; 0: none).  The sequence that writes sign bits and the one that reads them may be
  * dispatched to different kernel forms: use the bits only if both report the same tag, else pass the mask tensors. */
 int srk_conv3x3_seq_signs_tag(const srk_conv_args* args, int n);
+/* dispatch generation: a process-wide counter that moves whenever the kernel form a launch takes may have changed without the caller
+ * asking -- every srk_debug_set_* that selects a kernel form, srk_debug_chain_set, srk_chain_recover, and the sequence call that ends the
+ * chain forms' rest after a recovered time-out (it moves on that call, so the next query already sees it).  A caller that caches an
+ * answer that depends on the dispatch (a sign-bit layout tag) keys it with this value. */
+unsigned long long srk_dispatch_generation(void);
 
 int srk_conv3x3(const srk_conv_args* a, void* stream);
 /* n of them launched back to back on `stream`, in array order, from ONE call: the five forward (or five data-gradient) convolutions of

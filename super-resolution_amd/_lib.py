@@ -26,6 +26,7 @@ EXPORTS = [
     "srk_debug_hold_cus", "srk_debug_poison_lds", "srk_adam_count_step", "srk_debug_chain_inject_fault_async", "srk_debug_chain_skew",
     "srk_tconv2x2_fwd", "srk_tconv2x2_dgrad", "srk_tconv2x2_wgrad",
     "srk_sort_cut", "srk_sinkhorn_fwd", "srk_sinkhorn_bwd", "srk_sinkhorn_plan", "srk_scatter_rows",
+    "srk_dispatch_generation",
 ]
 SORT_CUT_MAX = 65536
 ERR_CHAIN_TIMEOUT = -6
@@ -89,15 +90,6 @@ class AdamEntry(C.Structure):
 
 
 _lib = None
-dispatch_gen = 0
-
-
-def _bumping(fn):
-    def call(*a):
-        global dispatch_gen
-        dispatch_gen += 1
-        return fn(*a)
-    return call
 
 
 def lib():
@@ -199,12 +191,9 @@ def lib():
         L.srk_debug_hold_cus.argtypes = [C.c_int, C.c_int, _fp]
         L.srk_debug_poison_lds.argtypes = [_fp]
         L.srk_adam_count_step.argtypes = [_fp, _fp, _fp, _fp]
-        # whatever changes which kernel form a launch takes bumps dispatch_gen: callers that cache a dispatch-dependent answer (the engine's
-        # sign-bit decisions) key it with the generation
         L.srk_debug_set_h16_chain_m16.argtypes = [C.c_int]
-        for name in ("srk_debug_set_h16_mt", "srk_debug_set_h16_chain", "srk_debug_set_h16_chain_m16", "srk_debug_set_w42_chain", "srk_debug_set_wino42_nmt",
-                     "srk_chain_recover", "srk_debug_chain_set"):
-            setattr(L, name, _bumping(getattr(L, name)))
+        L.srk_dispatch_generation.argtypes = []
+        L.srk_dispatch_generation.restype = C.c_ulonglong
         _lib = L
     return _lib
 
@@ -241,6 +230,13 @@ def _poison():
 def poison_lds():
     """test aid (srk_debug_poison_lds): NaN bit patterns into the whole LDS of every CU, on the current stream"""
     check(lib().srk_debug_poison_lds(stream_ptr()), "srk_debug_poison_lds")
+
+
+def dispatch_generation() -> int:
+    """srk_dispatch_generation: moves whenever the kernel form a launch takes may have changed (debug setters, srk_debug_chain_set,
+    srk_chain_recover, and the sequence call that ends the chain forms' rest inside the library).  Callers that cache a dispatch-dependent
+    answer (the engine's sign-bit layout tags) key it with this value."""
+    return int(lib().srk_dispatch_generation())
 
 
 def chain_stats() -> dict:

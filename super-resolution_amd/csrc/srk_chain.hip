@@ -1,6 +1,7 @@
 // srk_chain.hip -- host side of the chain kernels (srk_chain.h): the per-device flag array, the time-out word, the launch epoch and
 // the one-chain-kernel-in-flight rule.
 #include "srk_chain.h"
+#include <atomic>
 #include <mutex>
 #include <stdio.h>
 #include <stdlib.h>
@@ -24,7 +25,14 @@ struct ChainDev {
 };
 ChainDev g_dev[16];
 std::mutex g_mu;
+std::atomic<unsigned long long> g_dispatch_gen{0};
 
+}  // namespace
+
+void srk_dispatch_bump() { g_dispatch_gen.fetch_add(1); }
+extern "C" unsigned long long srk_dispatch_generation(void) { return g_dispatch_gen.load(); }
+
+namespace {
 unsigned wait_ticks_from_env() {
   const char* e = getenv("SRK_CHAIN_WAIT_MS");          // bound of every wait of a chain launch
   double ms = e ? atof(e) : 50.0;
@@ -111,14 +119,15 @@ void skew_from_env(ChainDev* D) {
   D->skew_read = true;
 }
 }  // namespace
-// back-off after a recovered time-out: true while the chain forms rest (srk_chain_recover); `tick` counts one sequence call off
+// back-off after a recovered time-out: true while the chain forms rest (srk_chain_recover); `tick` counts one sequence call off.  The
+// tick that ends the rest moves the dispatch generation: this call still rests, the next sequence call may go out as a chain.
 bool srk_chain_resting(bool tick) {
   std::lock_guard<std::mutex> lk(g_mu);
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return false;
   ChainDev& D = g_dev[dev];
   if (D.off_calls <= 0) return false;
-  if (tick) --D.off_calls;
+  if (tick && --D.off_calls == 0) srk_dispatch_bump();
   return true;
 }
 
@@ -200,6 +209,7 @@ int srk_chain_end(hipStream_t st, bool launched) {
 // keeps timing out, one that was only busy once gets its fast path back).  Returns the fault code that was pending (0: none) or < 0.
 extern "C" int srk_chain_recover(void) {
   std::lock_guard<std::mutex> lk(g_mu);
+  srk_dispatch_bump();
   ChainDev* D = chain_dev();
   if (!D) return 0;
   if (hipDeviceSynchronize() != hipSuccess) return SRK_ERR_LAUNCH;
@@ -264,6 +274,7 @@ extern "C" int srk_debug_hold_cus(int workgroups, int usec, void* stream) {
 // epoch / census count as if `epoch` convs had been chained (to cross SRK_CHAIN_WRAP within a test); clears the back-off when off == 0
 extern "C" int srk_debug_chain_set(unsigned epoch, long off_calls) {
   std::lock_guard<std::mutex> lk(g_mu);
+  srk_dispatch_bump();
   ChainDev* D = chain_dev();
   if (!D) return SRK_ERR_UNSUPPORTED;
   if (hipDeviceSynchronize() != hipSuccess) return SRK_ERR_LAUNCH;

@@ -1530,7 +1530,7 @@ extern "C" int srk_debug_set_h16_stamps(void* p) {
 }
 #endif
 
-extern "C" int srk_debug_set_h16_mt(int mt) { g_h16_mt = (mt == 1 || mt == 2 || mt == 4) ? mt : 0; return SRK_OK; }
+extern "C" int srk_debug_set_h16_mt(int mt) { g_h16_mt = (mt == 1 || mt == 2 || mt == 4) ? mt : 0; srk_dispatch_bump(); return SRK_OK; }
 
 // Form of the kernel: 16-row tiles (MT = 4: fewer halo rows, weight reads and barriers per MFMA; one workgroup per CU) when they
 // fill the chip (>= 200 workgroups), else the shared-CU form (8-row tiles, two workgroups per CU; at the c4 trunk it runs a
@@ -1605,14 +1605,14 @@ bool h16_chain_eligible(const srk_conv_args* args, int n, int mode) {
 }
 }  // namespace
 
-extern "C" int srk_debug_set_h16_chain(int mode) { g_h16_chain = (mode >= 0 && mode <= 2) ? mode : 1; return SRK_OK; }
+extern "C" int srk_debug_set_h16_chain(int mode) { g_h16_chain = (mode >= 0 && mode <= 2) ? mode : 1; srk_dispatch_bump(); return SRK_OK; }
 // MFMA shape of the chain kernel: 1 (default, SRK_H16_CHAIN_M16) = 16x16x32, weights as the row operand, epilogue without LDS; 0 = 32x32x16
 static int g_h16_chain_m16 = -1;
 static bool h16_chain_m16() {
   if (g_h16_chain_m16 < 0) { const char* e = getenv("SRK_H16_CHAIN_M16"); g_h16_chain_m16 = e ? (atoi(e) != 0) : 1; }
   return g_h16_chain_m16 != 0;
 }
-extern "C" int srk_debug_set_h16_chain_m16(int on) { g_h16_chain_m16 = on ? 1 : 0; return SRK_OK; }
+extern "C" int srk_debug_set_h16_chain_m16(int on) { g_h16_chain_m16 = on ? 1 : 0; srk_dispatch_bump(); return SRK_OK; }
 
 // 1: the sequence goes out as ONE chain launch; 0: not eligible (the caller launches the convs one by one)
 int srk_conv_h16_chain_would(const srk_conv_args* args, int n) {

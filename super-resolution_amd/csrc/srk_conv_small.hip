@@ -215,7 +215,7 @@ bool aligned16(const float* p, int ldc, int coff) { return !p || (((ldc | coff) 
 // Which of the kernels above serves a direct-format (wp_format 0), stride-1, plain-input convolution with <= 4 channels on one
 // side: 1 = conv3x3_cin_small_kernel<Cin>, 2 = conv3x3_cout_small_kernel<Cout>, 0 = neither (the MFMA kernels run it).
 static int g_small_mode = -1;          // 0 = off, 1 = when the tiles fill the chip (default), 2 = always (tests)
-extern "C" int srk_debug_set_conv_small(int mode) { g_small_mode = mode; return SRK_OK; }
+extern "C" int srk_debug_set_conv_small(int mode) { g_small_mode = mode; srk_dispatch_bump(); return SRK_OK; }
 
 int srk_conv_small_kind(const srk_conv_args& a) {
   if (g_small_mode < 0) { const char* e = getenv("SRK_CONV_SMALL"); g_small_mode = e ? atoi(e) : 1; }

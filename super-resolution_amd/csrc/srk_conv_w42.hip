@@ -544,7 +544,7 @@ __global__ __launch_bounds__(256) void conv3x3_f32_wino42_chain_kernel(const srk
 // M tiles per workgroup: the 32-row form when its workgroups fill the chip (>= 200) and pad the image no more than 16-row tiles
 // would, else the 16-row form.  SRK_WINO42_NMT = 1 | 2 / srk_debug_set_wino42_nmt force one (A/B measurements, tests).
 static int g_w42_nmt = -1;
-extern "C" int srk_debug_set_wino42_nmt(int nmt) { g_w42_nmt = (nmt == 1 || nmt == 2) ? nmt : 0; return SRK_OK; }
+extern "C" int srk_debug_set_wino42_nmt(int nmt) { g_w42_nmt = (nmt == 1 || nmt == 2) ? nmt : 0; srk_dispatch_bump(); return SRK_OK; }
 
 int srk_conv_wino42_nmt(const srk_conv_args& a) {
   if (g_w42_nmt < 0) { const char* e = getenv("SRK_WINO42_NMT"); g_w42_nmt = e ? atoi(e) : 0; }
@@ -572,7 +572,7 @@ int srk_launch_conv_wino42(const srk_conv_args& a, hipStream_t st) {
 
 // ---- the chain form: host side
 static int g_w42_chain = -1;      // 0: never, 1 (default): wherever the sequence is eligible
-extern "C" int srk_debug_set_w42_chain(int mode) { g_w42_chain = (mode == 0 || mode == 1) ? mode : 1; return SRK_OK; }
+extern "C" int srk_debug_set_w42_chain(int mode) { g_w42_chain = (mode == 0 || mode == 1) ? mode : 1; srk_dispatch_bump(); return SRK_OK; }
 
 static bool w42_chain_eligible(const srk_conv_args* args, int n) {
   if (g_w42_chain < 0) { const char* e = getenv("SRK_W42_CHAIN"); g_w42_chain = e ? atoi(e) : 1; }

@@ -21,5 +21,8 @@ static inline int srk_div_up(int v, int m) { return (v + m - 1) / m; }
   } while (0)
 
 
+// srk_chain.hip: moves srk_dispatch_generation (whatever changes the kernel form a launch takes calls it)
+void srk_dispatch_bump();
+
 // srk_tconv.hip: workspace of srk_tconv2x2_wgrad (srk_workspace_bytes(SRK_OP_TCONV2X2_WGRAD, ...))
 size_t srk_tconv2x2_wgrad_ws_bytes(int N, int H, int W, int Cin, int Cout);

@@ -909,7 +909,7 @@ int srk_wgrad_wino22_rows() {
   if (g_w22_rows < 0) { const char* e = getenv("SRK_WGRAD_W22_FORM"); g_w22_rows = e ? atoi(e) : W22_DEFAULT_FORM; if (g_w22_rows < 0 || g_w22_rows > 2) g_w22_rows = W22_DEFAULT_FORM; }
   return g_w22_rows;
 }
-extern "C" int srk_debug_set_wgrad_w22_form(int rows) { g_w22_rows = rows < 0 ? -1 : (rows > 2 ? 2 : rows); return SRK_OK; }
+extern "C" int srk_debug_set_wgrad_w22_form(int rows) { g_w22_rows = rows < 0 ? -1 : (rows > 2 ? 2 : rows); srk_dispatch_bump(); return SRK_OK; }
 
 int srk_launch_wgrad_wino22(const WBatch& B, float* part, float* pbias, hipStream_t st) {
   const int rows = srk_wgrad_wino22_rows();

@@ -398,9 +398,9 @@ class GeneratorEngine:
         # slice), where this sequence's launches offer them (16-bit storage: always; fp32: when it goes out as a chain kernel)
         signs, tag = None, 0
         if save and self.sign_bits and not self.use_graphs:
-            # (decided once per geometry, precision and DISPATCH GENERATION: _lib.dispatch_gen moves whenever a switch that changes the
-            # kernel form of a launch is thrown -- debug setters, a recovered chain fault)
-            key = ("f", N, H, W, F_, self.precision, calls[0][1].fmt, L.dispatch_gen)
+            # (decided once per geometry, precision and DISPATCH GENERATION: srk_dispatch_generation moves whenever the kernel form of a
+            # launch may change -- debug setters, a recovered chain fault, and the library's own end of the chain forms' rest after one)
+            key = ("f", N, H, W, F_, self.precision, calls[0][1].fmt, L.dispatch_generation())
             ent = self._signs_bytes.get(key)
             if ent is None:
                 ent = self._signs_bytes[key] = L.conv_seq_signs(calls)
@@ -433,7 +433,7 @@ class GeneratorEngine:
             if not use_signs:
                 break
             # (fp32: only the chain form of THIS sequence reads sign bits; decided once per geometry)
-            key = ("b", N, H, W, F_, self.precision, calls[0][1].fmt, L.dispatch_gen)
+            key = ("b", N, H, W, F_, self.precision, calls[0][1].fmt, L.dispatch_generation())
             ent = self._signs_bytes.get(key)
             if ent is None:
                 ent = self._signs_bytes[key] = L.conv_seq_signs(calls + [(View(E, 0, 5 * F_), self.wb(pk.bwd[0]), None, gx_out,
